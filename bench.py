@@ -2,7 +2,13 @@
 """bench.py -- headline metric of BASELINE.json: Mpixels/s JPEG encode of 8320x40000 RGB8, q95, 4:2:2, optimised
 Huffman (reference README.md:48 config), device-resident input -> device-resident JFIF bitstream.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+
+A plain run does only what `value` needs: it sets up, runs W warm-up steps (and the settling rounds below), times K steps and prints
+the line -- `value`, `ms_per_step` (one timed step) and the size and CRC of the last step's file. Everything else the line can carry
+(copy ceiling, per-kernel and stage-A passes, rooflines, clock probes, single-image time, the extra sections, golden and PSNR checks,
+CPU baselines, and at N > 1 the per-root file checks, latency and put rate) runs only with --full. --dump-outputs DIR writes the last
+timed step's file to DIR (dump_outputs); the synthetic input is fixed, so the same arguments give the same inputs in every run.
 
 N > 1 launches ITSELF: the process started by the command line never touches a GPU; it starts N fresh child processes (one
 rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, RCCL between them), relays rank 0's JSON line
@@ -16,7 +22,7 @@ launcher's other ranks leave at once, so both command shapes run the same childr
 A "step" is one whole encode of the image. On one GPU (round 4) the timed loop runs the transform of image i on one HIP stream
 and the entropy stage (tables, Huffman coding, size scan, stuffing + compaction) of image i-1 on a second one, three handles taking
 turns, so the issue-bound transform and the latency-bound coder share the machine (--loop overlap, the default; --loop
-tables-ahead / one-stream / two-streams are the earlier rounds' loops). Everything the line says about a SINGLE kernel -- `roofline`,
+tables-ahead / one-stream / two-streams are the earlier rounds' loops). With --full, everything the line says about a SINGLE kernel -- `roofline`,
 `stage_roofline`, `stage_ms` -- comes from a short separate pass right AFTER the timed region in which every kernel of an image runs alone
 on one stream, labelled as such, followed by a stage-A-alone pass (the transform without the fused statistics, the kernel the
 north-star's 70 % is about). The shader clock needs tens of milliseconds of load to settle, more than W = 5 warm-up steps last: behind
@@ -96,7 +102,17 @@ def parse():
                          "behind the next image's all-reduce (default); per-slot = one communicator per image slot (experiment: concurrent "
                          "communicators are not ordered against each other across ranks)")
     ap.add_argument("--no-fallback", action="store_true", help="N > 1: fail instead of retrying with the next gather of the ladder")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: copy ceiling, per-kernel and stage-A passes, "
+                    "single-image time, the extra sections, golden and PSNR checks, CPU baselines; N > 1: the per-root file checks, "
+                    "latency, put rate and stage table too (default: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's JPEG file to "
+                    "DIR as float .npy arrays (dump_outputs), so that two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)     # the ranks of N > 1 run with the repository as their cwd
+    return args
 
 
 def algorithmic_bytes_per_pixel(css, ratio):
@@ -284,7 +300,7 @@ def supervise(args, world, launcher):
                     runs["sendrecv"] = {"failed": reason2}
                 out["gather_runs"] = runs
                 out["gather_runs_note"] = "two complete runs with fresh ranks, one per gather; this line is the faster one's"
-            if not getattr(args, "no_cpu_baseline", True) and "jpeg_crc32" in out and "cpu_baseline" not in out:
+            if getattr(args, "full", False) and not getattr(args, "no_cpu_baseline", True) and "jpeg_crc32" in out and "cpu_baseline" not in out:
                 # libjpeg-turbo on the box's host cores in the same run, at every N: the supervisor holds no GPU and its ranks are gone
                 try:
                     out.update(cpu_baseline_fields(args, not args.no_optimize, out["config"]["restart_interval"], out["jpeg_crc32"], out["jpeg_bytes"]))
@@ -383,8 +399,7 @@ def _smi_clocks():
         # script (env -> python3): that chain of exec()s from GPU-initialised processes is what the GPU boxes refuse
         return {"note": "not queried under a profiler"}
     try:
-        env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD"}
-        r = subprocess.run(["rocm-smi", "--showclocks", "--showmaxpower", "--showpower", "--showperflevel"], capture_output=True, text=True, timeout=20, env=env)
+        r = subprocess.run(["rocm-smi", "--showclocks", "--showmaxpower", "--showpower", "--showperflevel"], capture_output=True, text=True, timeout=20)
         for key, pat in (("sclk_MHz", r"GPU\[0\].*sclk clock level.*\((\d+)Mhz\)"), ("mclk_MHz", r"GPU\[0\].*mclk clock level.*\((\d+)Mhz\)"),
                          ("power_cap_W", r"GPU\[0\].*Max Graphics Package Power \(W\):\s*([\d.]+)"),
                          ("socket_power_W", r"GPU\[0\].*Current Socket Graphics Package Power \(W\):\s*([\d.]+)"),
@@ -396,6 +411,12 @@ def _smi_clocks():
         out["error"] = repr(ex)[:120]
     out["note"] = "rocm-smi, read while the GPU is idle between the passes (sclk then shows a sleep state): informational"
     return out
+
+
+_PIPELINE = {"overlap": "transform of image i on one stream, entropy stage (tables, coder, scan, compaction) of image i-1 on a second one; three handles",
+             "tables-ahead": "image i's table build (one workgroup) on a side stream under image i-1's entropy coder; all other kernels of all images on one stream",
+             "two-streams": "two handles, each image entirely on its own stream", "one-stream": "two handles, every kernel in issue order on one stream",
+             "progressive": "one handle; the ten scans on the library's four internal streams"}
 
 
 def worker_one_gpu(args):
@@ -419,7 +440,8 @@ def worker_one_gpu(args):
     strips = [sharded.HipStripEncoder(torch, e, d_img, args.fmt, shared_statistics=False) for e in encs]
     torch.cuda.synchronize()
     clocks = [_clock(torch, mij, "start (device idle before)")]
-    copy_gbs, copy_lib_gbs = hbm_copy_ceiling(torch, mij, dev)
+    copy_gbs, copy_lib_gbs = hbm_copy_ceiling(torch, mij, dev) if args.full else (None, None)
+    streams = 1 if loop in ("one-stream", "progressive") else 2
 
     # ---- the timed loop ---------------------------------------------------------------------------------------------------
     side = torch.cuda.Stream() if loop in ("overlap", "tables-ahead", "two-streams") else None
@@ -465,7 +487,7 @@ def worker_one_gpu(args):
     # the stage-A pass's encoder (fixed tables) is made here: allocating its workspace between the passes below would idle the device
     # for long enough that the clock falls back (seen: 0.448 ms average over launches whose fastest took 0.414)
     ea = sa = ea2 = sa2 = None
-    if args.stage_a_pass > 0 and not args.progressive and optimize:
+    if args.full and args.stage_a_pass > 0 and not args.progressive and optimize:
         ea = sharded.make_hip_strip_encoder(torch, W, H, args.quality, False, args.css, 0, 1, 0, args.fmt, restart_interval=args.restart_interval)
         sa = sharded.HipStripEncoder(torch, ea, d_img, args.fmt, shared_statistics=False)
         ea2 = sharded.make_hip_strip_encoder(torch, W, H, args.quality, False, args.css, 0, 1, 0, args.fmt, restart_interval=args.restart_interval)
@@ -501,9 +523,16 @@ def worker_one_gpu(args):
     jpeg_t = drain()
     fence()
     dt = time.perf_counter() - t0
-    clocks.append(_clock(torch, mij, "right after the timed region"))
     ms_per_step = dt / args.steps * 1e3
     value = (W * H / 1e6) / (ms_per_step / 1e3)
+    if not args.full:          # a plain run: the line of the timed loop and nothing else
+        ctx = dict(world=1, W=W, H=H, optimize=optimize, geo=geo, rows=rows, value=value, ms_per_step=ms_per_step, jpeg_t=jpeg_t,
+                   n_handles=n_handles, gather_mode=None, dpipe=None, root_files=None, streams=streams, pipeline=_PIPELINE[loop])
+        rc = report(args, torch, mij, ctx, {"loop": loop, "untimed_steps": args.warmup + settle_steps})
+        for e in encs:
+            e.close()
+        return rc
+    clocks.append(_clock(torch, mij, "right after the timed region"))
     jpeg_keep = jpeg_t.clone()
 
     # ---- per-kernel pass: every kernel of an image alone on ONE stream, events around each (the library's own, mij_stage_times) ----
@@ -580,11 +609,7 @@ def worker_one_gpu(args):
     ctx = dict(world=1, rank=0, W=W, H=H, optimize=optimize, geo=geo, rows=rows, value=value, ms_per_step=ms_per_step, jpeg_t=jpeg_keep,
                stages=stages, n_handles=n_handles, gather_mode=None, dpipe=None, copy_gbs=copy_gbs, copy_lib_gbs=copy_lib_gbs, d_img=d_img,
                root_files=None, want_put=False, one_device=False, rccl_ranks=None, single_ms=None, put_rate=None,
-               streams=(1 if loop in ("one-stream", "progressive") else 2),
-               pipeline={"overlap": "transform of image i on one stream, entropy stage (tables, coder, scan, compaction) of image i-1 on a second one; three handles",
-                         "tables-ahead": "image i's table build (one workgroup) on a side stream under image i-1's entropy coder; all other kernels of all images on one stream",
-                         "two-streams": "two handles, each image entirely on its own stream", "one-stream": "two handles, every kernel in issue order on one stream",
-                         "progressive": "one handle; the ten scans on the library's four internal streams"}[loop])
+               streams=streams, pipeline=_PIPELINE[loop])
     extra = {"loop": loop,
              "per_kernel_pass": {"images": kp, "streams": 1, "file_identical_to_timed_loop": None,
                                  "note": "`roofline`, `stage_roofline` and `stage_ms` come from this pass: one image at a time on ONE stream, every kernel "
@@ -969,7 +994,7 @@ def worker_ranks(args):
             return sharded.encode_step_progressive(torch, dist, strip, cache, st)
         return sharded.encode_step(torch, dist, strip, optimize, cache, st)
 
-    copy_gbs, copy_lib_gbs = hbm_copy_ceiling(torch, mij, dev) if rank == 0 else (None, None)
+    copy_gbs, copy_lib_gbs = hbm_copy_ceiling(torch, mij, dev) if rank == 0 and args.full else (None, None)
     cache, stage_acc = {"device": dev}, {}
 
     # Images in flight. Every step still produces a complete file inside the timed region.
@@ -1054,7 +1079,7 @@ def worker_ranks(args):
             raise SystemExit("put pipeline (%s): the %d roots assembled different files: %s" % (what, dpipe.nroots, files))
         return files
 
-    root_files = verify_roots("before the timed region") if dpipe is not None else None
+    root_files = verify_roots("before the timed region") if dpipe is not None and args.full else None
     fence()
     _progress(rank, "warm-up done")
     t0 = time.perf_counter()
@@ -1086,9 +1111,22 @@ def worker_ranks(args):
         elif rank == 0:
             jpeg_keep = torch.empty(int(nb.item()), dtype=torch.uint8, device=dev)
             dist.recv(jpeg_keep, src=lr)
-    if dpipe is not None:
+    if root_files is not None:
         # the same per-root check on images assembled AFTER the timed region (buffers, mappings and streams as the loop left them)
         root_files = root_files + verify_roots("after the timed region")
+    if not args.full:          # a plain run: the line of the timed loop and nothing else
+        rc = 0
+        if rank == 0:
+            ctx = dict(world=world, W=W, H=H, optimize=optimize, geo=geo, rows=rows, value=value, ms_per_step=ms_per_step, jpeg_t=jpeg_keep,
+                       n_handles=n_handles, gather_mode=gather_mode, dpipe=dpipe, root_files=None, want_put=want_put, one_device=one_device,
+                       rccl_ranks=rccl_ranks, streams=n_handles if dpipe is not None else 1, pipeline=None)
+            rc = report(args, torch, mij, ctx, {})
+        for e in encs:
+            if e is not None:
+                e.close()
+        dist.barrier()
+        dist.destroy_process_group()
+        return rc
     # ONE image alone through the same path, start to complete file (what a caller with a single image waits for; the
     # `value` above is the rate with several images in flight). Max over ranks, median of five.
     lat = []
@@ -1179,20 +1217,72 @@ def worker_ranks(args):
 
 
 def report(args, torch, mij, c, extra):
-    """Rank 0: verify the file, build and print the JSON line."""
-    world, W, H, optimize, geo, rows = c["world"], c["W"], c["H"], c["optimize"], c["geo"], c["rows"]
-    dpipe, root_files, stages, copy_gbs, copy_lib_gbs = c["dpipe"], c["root_files"], c["stages"], c["copy_gbs"], c["copy_lib_gbs"]
+    """Rank 0: verify the file, build and print the JSON line (--full: with the analysis and the checks of the whole run)."""
+    world, W, H, optimize, geo = c["world"], c["W"], c["H"], c["optimize"], c["geo"]
+    dpipe, root_files = c["dpipe"], c["root_files"]
     jpeg = c["jpeg_t"].cpu().numpy().tobytes()
     fingerprint = "%08x:%d" % (zlib.crc32(jpeg), len(jpeg))
     if root_files is not None and set(root_files) != {fingerprint}:
         raise SystemExit("put pipeline: the files collected from the roots (%s) differ from the timed region's file (%s)" % (root_files, fingerprint))
+    ratio = len(jpeg) / (3.0 * W * H)
+    out = {
+        "metric": "Mpixels/s encode (+PSNR, ratio) 8320x40000 q95 4:2:2 @1/2/4/8 GPU",
+        "value": round(c["value"], 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(c["ms_per_step"], 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "u8", "data": "synthetic",
+        "config": {"workload": "%dx%d RGB8 (%s interleaved, device resident) -> %s JFIF, q%d, 4:%s:%s, %s Huffman, "
+                               "DRI=%d MCUs" % (W, H, args.fmt.upper(), "progressive (SOF2)" if args.progressive else "baseline", args.quality,
+                                                args.css[1], args.css[2], "optimised" if optimize else "fixed", geo["restart_interval"]),
+                   "parallelism": "strips%d" % world, "restart_interval": geo["restart_interval"],
+                   "images_in_flight": c["n_handles"], "gather": c["gather_mode"] if os.environ.get("MIJ_BENCH_NO_PIPELINE") != "1" or world == 1 else "serial",
+                   "comms": (dpipe.comms if dpipe is not None else None),
+                   "root": (None if dpipe is None else ("rank 0" if args.fixed_root else "rotating over the ranks, image by image")),
+                   "streams": c["streams"], "pipeline": c["pipeline"]},
+        "jpeg_bytes": len(jpeg), "ratio": round(ratio, 5), "jpeg_crc32": "%08x" % zlib.crc32(jpeg),
+    }
+    if args.full:
+        out.update(analysis(args, mij, c, extra, jpeg, ratio))
+    out.update(extra)
+    out["library_source_hash"] = mij.library_source_hash()
+    golden = golden_fingerprint(args, optimize, geo["restart_interval"]) if args.full else None
+    if golden is not None:          # the committed fingerprint of this exact configuration (tests/golden/, computed on the CPU)
+        out["golden_match"] = golden == (out["jpeg_crc32"], out["jpeg_bytes"])
+    if world > 1:
+        out["rccl_ranks"] = c["rccl_ranks"]
+        out["collective_backend"] = "gloo (one-device rehearsal)" if c["one_device"] else "nccl (RCCL)"
+        if args.full:
+            out["single_image_latency_ms"] = round(c["single_ms"], 4) if c["single_ms"] is not None else None
+            out["single_image_latency_note"] = "one image alone, issue to complete file on its root, max over ranks, median of 5"
+            out["put_GB/s"] = c["put_rate"]
+        if root_files is not None:
+            out["files_verified"] = {"roots": dpipe.nroots, "images": len(root_files), "identical_to_timed_file": True,
+                                     "when": "one image per root before the timed region and one per root after it"}
+        if c["want_put"] and dpipe is None:
+            out["gather_note"] = "the output buffers could not be peer-mapped (hipIpc*): every rank took send/recv"
+    if args.full and not args.no_psnr:
+        out["psnr_db"], out["psnr_note"], pillow_crc = _psnr_check(jpeg, W, H, args.fmt, c["d_img"] if world == 1 else None)
+        own = out.get("decode", {}).get("own_file")
+        if own is not None:        # the library's decode of the timed region's file against libjpeg-turbo's decode of the same file, by CRC of the RGB8 image
+            own["pillow_decoded_crc32"] = pillow_crc
+            own["identical_to_pillow"] = own["decoded_crc32"] == pillow_crc
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        out.update(cpu_baseline_fields(args, optimize, geo["restart_interval"], out["jpeg_crc32"], out["jpeg_bytes"]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, jpeg)
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+def analysis(args, mij, c, extra, jpeg, ratio):
+    """--full: the per-kernel pass's file checked against the timed loop's; rooflines of the kernels from the pass's stage times."""
+    world, W, optimize, rows = c["world"], c["W"], c["optimize"], c["rows"]
+    stages, copy_gbs, copy_lib_gbs = c["stages"], c["copy_gbs"], c["copy_lib_gbs"]
     kp_file = extra.pop("_kp_file", None)
     if kp_file is not None:
         same = kp_file.cpu().numpy().tobytes() == jpeg
         extra["per_kernel_pass"]["file_identical_to_timed_loop"] = same
         if not same:
             raise SystemExit("the one-stream pass and the timed loop produced different files")
-    ratio = len(jpeg) / (3.0 * W * H)
     strip_px = rows * W
     bpp = algorithmic_bytes_per_pixel(args.css, ratio)
     kname = {"transform": "k_transform", "entropy": "k_encode", "compact": "k_compact"}
@@ -1269,49 +1359,23 @@ def report(args, torch, mij, c, extra):
     else:   # --progressive: twenty lane-per-interval passes sequenced by the host; not a roofline-shaped workload
         roofline = {"bound": "hbm", "kernel": "k_prog_encode", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None}
         extra.pop("stage_A_alone", None)
-    out = {
-        "metric": "Mpixels/s encode (+PSNR, ratio) 8320x40000 q95 4:2:2 @1/2/4/8 GPU",
-        "value": round(c["value"], 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(c["ms_per_step"], 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "u8", "data": "synthetic",
-        "config": {"workload": "%dx%d RGB8 (%s interleaved, device resident) -> %s JFIF, q%d, 4:%s:%s, %s Huffman, "
-                               "DRI=%d MCUs" % (W, H, args.fmt.upper(), "progressive (SOF2)" if args.progressive else "baseline", args.quality,
-                                                args.css[1], args.css[2], "optimised" if optimize else "fixed", geo["restart_interval"]),
-                   "parallelism": "strips%d" % world, "restart_interval": geo["restart_interval"],
-                   "images_in_flight": c["n_handles"], "gather": c["gather_mode"] if os.environ.get("MIJ_BENCH_NO_PIPELINE") != "1" or world == 1 else "serial",
-                   "comms": (dpipe.comms if dpipe is not None else None),
-                   "root": (None if dpipe is None else ("rank 0" if args.fixed_root else "rotating over the ranks, image by image")),
-                   "streams": c["streams"], "pipeline": c["pipeline"]},
-        "jpeg_bytes": len(jpeg), "ratio": round(ratio, 5), "jpeg_crc32": "%08x" % zlib.crc32(jpeg),
+    return {
         "roofline": roofline, "hbm_copy_ceiling_GB/s": round(copy_gbs, 1) if copy_gbs else None,
         "hbm_copy_ceiling_note": "own 16-B/lane copy kernel (k_copy16), read + write bytes; torch copy_ on the same box: %s GB/s" % (round(copy_lib_gbs, 1) if copy_lib_gbs else None), "stage_roofline": stage_roof, "stage_ms": {k: round(v, 4) for k, v in stages.items()},
     }
-    out.update(extra)
-    out["library_source_hash"] = lib_hash
-    golden = golden_fingerprint(args, optimize, geo["restart_interval"])
-    if golden is not None:          # the committed fingerprint of this exact configuration (tests/golden/, computed on the CPU)
-        out["golden_match"] = golden == (out["jpeg_crc32"], out["jpeg_bytes"])
-    if world > 1:
-        out["rccl_ranks"] = c["rccl_ranks"]
-        out["collective_backend"] = "gloo (one-device rehearsal)" if c["one_device"] else "nccl (RCCL)"
-        out["single_image_latency_ms"] = round(c["single_ms"], 4) if c["single_ms"] is not None else None
-        out["single_image_latency_note"] = "one image alone, issue to complete file on its root, max over ranks, median of 5"
-        out["put_GB/s"] = c["put_rate"]
-        if root_files is not None:
-            out["files_verified"] = {"roots": dpipe.nroots, "images": len(root_files), "identical_to_timed_file": True,
-                                     "when": "one image per root before the timed region and one per root after it"}
-        if c["want_put"] and dpipe is None:
-            out["gather_note"] = "the output buffers could not be peer-mapped (hipIpc*): every rank took send/recv"
-    if not args.no_psnr:
-        out["psnr_db"], out["psnr_note"], pillow_crc = _psnr_check(jpeg, W, H, args.fmt, c["d_img"] if world == 1 else None)
-        own = out.get("decode", {}).get("own_file")
-        if own is not None:        # the library's decode of the timed region's file against libjpeg-turbo's decode of the same file, by CRC of the RGB8 image
-            own["pillow_decoded_crc32"] = pillow_crc
-            own["identical_to_pillow"] = own["decoded_crc32"] == pillow_crc
-    if world == 1 and not args.no_cpu_baseline:
-        out.update(cpu_baseline_fields(args, optimize, geo["restart_interval"], out["jpeg_crc32"], out["jpeg_bytes"]))
-    print(json.dumps(out), flush=True)
-    return 0
+
+
+def dump_outputs(d, jpeg, head=1 << 22, sample=1 << 22, seed=0):
+    """What the timed path returned in its last step -- the JPEG file -- as float arrays that two builds' runs can be compared with
+    (32 MB at most): jpeg_info = [bytes, CRC-32 of the whole file] (float64, exact), jpeg_head = its first `head` bytes (markers,
+    tables and the start of the scan), jpeg_sample = `sample` bytes at sorted positions drawn from a fixed seed over the whole file."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    b = np.frombuffer(jpeg, np.uint8)
+    pos = np.sort(np.random.default_rng(seed).integers(0, len(b), size=sample))
+    np.save(os.path.join(d, "jpeg_info.npy"), np.array([len(b), zlib.crc32(jpeg)], np.float64))
+    np.save(os.path.join(d, "jpeg_head.npy"), b[:head].astype(np.float32))
+    np.save(os.path.join(d, "jpeg_sample.npy"), b[pos].astype(np.float32))
 
 
 def cpu_baseline_fields(args, optimize, restart_interval, jpeg_crc32, jpeg_bytes):

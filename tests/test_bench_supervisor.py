@@ -213,7 +213,52 @@ def test_supervisor_adds_the_cpu_legs_at_n_gt_1(bench, capsys, monkeypatch):
     script = pathlib.Path(bench._log).parent / "child2.py"
     script.write_text(child)
     monkeypatch.setattr(bench, "_child_argv", lambda mode: [sys.executable, str(script), mode])
-    rc, line, log = _run(bench, capsys, {}, monkeypatch, world=2, no_cpu_baseline=False, no_optimize=False, gather="sendrecv")
+    rc, line, log = _run(bench, capsys, {}, monkeypatch, world=2, full=True, no_cpu_baseline=False, no_optimize=False, gather="sendrecv")
     assert rc == 0 and line["cpu_baseline"]["crc_seen"] == "47e0cdfa"
-    rc, line, log = _run(bench, capsys, {}, monkeypatch, world=2, no_cpu_baseline=True, no_optimize=False, gather="sendrecv")
+    rc, line, log = _run(bench, capsys, {}, monkeypatch, world=2, full=True, no_cpu_baseline=True, no_optimize=False, gather="sendrecv")
     assert rc == 0 and "cpu_baseline" not in line
+    rc, line, log = _run(bench, capsys, {}, monkeypatch, world=2, full=False, no_cpu_baseline=False, no_optimize=False, gather="sendrecv")
+    assert rc == 0 and "cpu_baseline" not in line          # a plain run (no --full) measures the GPU loop only
+
+
+def test_plain_line_and_dumped_outputs(monkeypatch, tmp_path, capsys):
+    """report() of a plain run (no --full): the headline fields only; --dump-outputs writes the timed loop's last file as float
+    arrays -- its size and CRC exactly, its first 4 MiB and a sample at seeded positions -- the same for the same file, within 64 MB."""
+    import importlib
+    import zlib
+    import numpy as np
+    b = importlib.import_module("bench")
+    out_dir = tmp_path / "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--width", "64", "--height", "48", "--dump-outputs", str(out_dir)])
+    args = b.parse()
+    assert not args.full and args.steps == 3 and os.path.isabs(args.dump_outputs)
+    jpeg = np.random.default_rng(1).integers(0, 256, size=(5 << 20) + 3, dtype=np.uint8)
+
+    class File:          # stands in for the device tensor holding the file
+        def cpu(self):
+            return self
+
+        def numpy(self):
+            return jpeg
+
+    class Lib:
+        @staticmethod
+        def library_source_hash():
+            return "0" * 64
+
+    ctx = dict(world=1, W=64, H=48, optimize=True, geo={"restart_interval": 4}, rows=48, value=123.4, ms_per_step=0.5, jpeg_t=File(),
+               n_handles=3, gather_mode=None, dpipe=None, root_files=None, streams=2, pipeline="p")
+    assert b.report(args, None, Lib, ctx, {"loop": "overlap", "untimed_steps": 7}) == 0
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["steps"] == 3 and line["ms_per_step"] == 0.5 and line["value"] == 123.4 and line["dtype"] == "u8" and line["higher_is_better"] is True
+    assert line["jpeg_bytes"] == jpeg.size and line["jpeg_crc32"] == "%08x" % zlib.crc32(jpeg.tobytes())
+    assert not {"roofline", "stage_ms", "hbm_copy_ceiling_GB/s", "psnr_db", "golden_match", "cpu_baseline"} & set(line)
+    got = {f: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+    assert sorted(got) == ["jpeg_head.npy", "jpeg_info.npy", "jpeg_sample.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["jpeg_info.npy"].tolist() == [jpeg.size, zlib.crc32(jpeg.tobytes())]
+    assert np.array_equal(got["jpeg_head.npy"], jpeg[:1 << 22].astype(np.float32))
+    assert got["jpeg_sample.npy"].shape == (1 << 22,) and set(np.unique(got["jpeg_sample.npy"])) <= set(range(256))
+    b.dump_outputs(str(tmp_path / "again"), jpeg.tobytes())
+    assert np.array_equal(np.load(tmp_path / "again" / "jpeg_sample.npy"), got["jpeg_sample.npy"])

@@ -20,7 +20,7 @@ def _bench(args, timeout=600):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
-SMALL = ["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-psnr", "--height", "4000", "--kernel-pass", "2", "--stage-a-pass", "2"]
+SMALL = ["--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-psnr", "--height", "4000", "--kernel-pass", "2", "--stage-a-pass", "2"]
 
 
 @pytest.fixture(scope="module")
@@ -69,7 +69,7 @@ def test_fixed_tables_and_progressive_lines():
 def test_driver_line_carries_every_single_gpu_config_and_both_decoders():
     """Round 5: the default workload's line holds BASELINE configs 3 and 5 and both decoders, each checked against a committed golden or
     against a stock decoder inside the run (the CPU legs are switched off here; the driver's command runs them too)."""
-    d = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--kernel-pass", "2", "--stage-a-pass", "2"], timeout=900)
+    d = _bench(["--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--kernel-pass", "2", "--stage-a-pass", "2"], timeout=900)
     assert d["golden_match"] is True and d["untimed_steps"] >= 1
     rows = d["configs"]["table1"]["rows"]
     assert sorted(rows) == ["411", "420", "422", "440", "444"]
@@ -90,3 +90,22 @@ def test_driver_line_carries_every_single_gpu_config_and_both_decoders():
     if v is not None and v["model"] == "bound":          # (only when profiles/ holds the class file of THIS build)
         k = v["kernels"]["k_transform"]
         assert k["bound_ms"] < k["launch_ms"] and 2.0 <= k["bound_cycles_per_instruction"] <= 4.0 <= k["cycles_per_valu_instruction"] + 1.0
+
+
+def test_plain_run_times_the_loop_only_and_dumps_the_last_file(default_line, tmp_path):
+    """Without --full the line carries the headline and the file's fingerprint and nothing measured outside the timed loop; the file is
+    the full run's, and --dump-outputs writes the same arrays whatever the number of steps."""
+    import numpy as np
+    runs = []
+    for steps in (5, 3):
+        out = tmp_path / str(steps)
+        d = _bench(["--steps", str(steps), "--warmup", "2", "--height", "4000", "--dump-outputs", str(out)])
+        assert d["steps"] == steps and d["loop"] == "overlap" and d["ms_per_step"] > 0
+        assert abs(d["value"] - 8320 * 4000 / 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+        assert (d["jpeg_crc32"], d["jpeg_bytes"]) == (default_line["jpeg_crc32"], default_line["jpeg_bytes"])
+        assert not {"roofline", "stage_ms", "clock", "per_kernel_pass", "single_image_ms", "psnr_db", "golden_match", "cpu_baseline"} & set(d)
+        arrays = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert arrays["jpeg_info.npy"].tolist() == [d["jpeg_bytes"], int(d["jpeg_crc32"], 16)]
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        runs.append(arrays)
+    assert all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])

@@ -228,7 +228,7 @@ def _bench(args, env_extra=None, launcher=False, timeout=900):
 
 @pytest.fixture(scope="module")
 def one_gpu_line():
-    d, _ = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-psnr", "--height", "4000"])
+    d, _ = _bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-psnr", "--height", "4000"])
     assert d["n_gpus"] == 1 and "launcher" not in d          # N = 1 runs in the process of the command line, as ever
     # round 4: the loop behind `value` overlaps two images on two streams; per-kernel figures come from a separate one-stream pass
     assert d["loop"] == "overlap" and d["config"]["streams"] == 2 and d["config"]["images_in_flight"] == 3
@@ -247,7 +247,7 @@ def test_bench_multi_rank_rehearsal(one_gpu_line, gather, comms):
     file. All forms of the step: four images in flight with the put gather and a rotating root (sharded.DevicePipeline, on
     one ordered communicator -- the default -- and on one communicator per slot), two in flight with send/recv
     (sharded.StripPipeline) and one at a time (sharded.encode_step)."""
-    d, _ = _bench(["--gpus", "3", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--height", "4000", "--gather", gather]
+    d, _ = _bench(["--full", "--gpus", "3", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--height", "4000", "--gather", gather]
                   + (["--comms", comms] if comms else []))
     assert d["n_gpus"] == 3 and d["steps"] == 4 and d["scaling"] == "strong" and d["value"] > 0
     assert d["config"]["parallelism"] == "strips3" and d["config"]["images_in_flight"] == {"put": 4, "sendrecv": 2, "serial": 1}[gather]

@@ -90,7 +90,7 @@ def run(extra):
     for name in list(VARIANTS) + [d for d in ("prev",) if os.path.exists(os.path.join(OUT, d, "libmijpeg.so"))]:
         lib = os.path.join(OUT, name, "libmijpeg.so")
         env = dict(os.environ, MIJ_LIB_PATH=lib)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-psnr"] + extra,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-psnr"] + extra,
                            capture_output=True, text=True, env=env)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])

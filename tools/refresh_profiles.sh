@@ -13,7 +13,8 @@ if [ "$what" = pmc ]; then
   cd /tmp && export TMPDIR=/tmp
   step "kernel trace: the driver's command (no CPU legs, no extra sections)"
   rm -rf $R/gpurun_out/prof_bench; mkdir -p $R/gpurun_out/prof_bench
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_bench -o bench --output-format csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-psnr --no-extra > $R/gpurun_out/prof_bench/log.txt 2>&1 || exit 1
+  P=$(dirname $O)/prof_bench
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $P -o bench --output-format csv -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-psnr --no-extra > $P/log.txt 2>&1 || exit 1
   cd $R
   step "pmc fetch";  bash tools/pmc_pass.sh fetch FETCH_SIZE >> $O/progress.txt 2>&1 || exit 1
   step "pmc write";  bash tools/pmc_pass.sh write WRITE_SIZE >> $O/progress.txt 2>&1 || exit 1
@@ -22,12 +23,12 @@ if [ "$what" = pmc ]; then
   python3 tools/hbm_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write gpurun_out/pmc_b gpurun_out/pmc_a > $O/hbm_traffic.json || exit 1
   python3 tools/pmc_summary.py gpurun_out/pmc_a gpurun_out/pmc_b > $O/pmc_sq_summary.txt
 elif [ "$what" = lines ]; then
-  step "bench: the driver's command";  timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench.err || exit 1
-  step "bench: 200 steps";             timeout -k 10 400 python3 bench.py --steps 200 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_200.json 2>> $O/bench.err || exit 1
-  step "bench: fixed tables";          timeout -k 10 300 python3 bench.py --steps 200 --no-optimize --no-cpu-baseline > $O/bench_fixed.json 2>> $O/bench.err || exit 1
-  step "bench: progressive";           timeout -k 10 300 python3 bench.py --steps 50 --progressive --no-cpu-baseline > $O/bench_prog.json 2>> $O/bench.err || exit 1
+  step "bench: 20 steps, every leg";  timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench.err || exit 1
+  step "bench: 200 steps";             timeout -k 10 400 python3 bench.py --full --steps 200 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_200.json 2>> $O/bench.err || exit 1
+  step "bench: fixed tables";          timeout -k 10 300 python3 bench.py --full --steps 200 --no-optimize --no-cpu-baseline > $O/bench_fixed.json 2>> $O/bench.err || exit 1
+  step "bench: progressive";           timeout -k 10 300 python3 bench.py --full --steps 50 --progressive --no-cpu-baseline > $O/bench_prog.json 2>> $O/bench.err || exit 1
   step "bench: progressive, 3 ranks on this one GPU (gloo rehearsal: correctness of the sharded path, not a rate)"
-  MIJ_BENCH_ONE_DEVICE=1 timeout -k 10 500 python3 bench.py --gpus 3 --steps 5 --warmup 1 --progressive --no-cpu-baseline > $O/bench_prog_3ranks_one_device.json 2>> $O/bench.err || exit 1
+  MIJ_BENCH_ONE_DEVICE=1 timeout -k 10 500 python3 bench.py --full --gpus 3 --steps 5 --warmup 1 --progressive --no-cpu-baseline > $O/bench_prog_3ranks_one_device.json 2>> $O/bench.err || exit 1
 else
   step "px cases";                     timeout -k 10 600 python3 tools/px_cases.py 2>/dev/null | grep -v "^\[px" > $O/px_cases.txt
   : > $O/px_thin.txt
